@@ -34,6 +34,9 @@ every operating point on that one index, engine and oracle; `qps_vs_recall_at_10
 the same 100 M index with refine_factor 10 / 25 over resident bf16 raw vectors, and flat C2
 (BASELINE.json configs[1]: 10 M x 768 bf16, 1024 queries, L2 and cosine) with the
 GEMM kernel's own roofline and a full-size parity check each.
+
+--dump-outputs DIR writes the last timed step's results (rowids, distances, counts) as DIR/<name>.npy; the inputs
+depend on the arguments only, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -47,6 +50,7 @@ if ROOT not in sys.path:
 
 SEED = 0x1A2CE
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def parse():
@@ -110,7 +114,37 @@ def parse():
     ap.add_argument("--c5-hugepages", type=int, default=0, help="back the C5 host column with MADV_HUGEPAGE memory (A/B of the PCIe gather)")
     ap.add_argument("--scan-variant", type=int, default=0)
     ap.add_argument("--slice-rows", type=int, default=0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (row ids, distances, counts) as "
+                         "DIR/<name>.npy so that two builds can be compared output for output (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.workload == "flat" or (a.workload == "c4" and a.gpus == 1 and not a.force_sharded_path)):
+        ap.error("--dump-outputs writes the results of the IVF-PQ timed path: not available with --workload flat "
+                 "or the single-GPU --workload c4 leg")
+    return a
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write `arrays` (name -> array, all with one row per query) as path/<name>.npy: integers as float64 (exact below
+    2^53), floats as float32.  When they would take more than `limit` bytes, a fixed, seeded sample of the queries is
+    written instead, with the sampled query positions in path/query_index.npy."""
+    import numpy as np
+    out = {}
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        out[name] = v.astype(np.float32 if v.dtype == np.float32 else np.float64)
+    n = len(next(iter(out.values())))
+    if sum(v.nbytes for v in out.values()) > limit:
+        per_query = sum(v.nbytes // n for v in out.values()) + 8  # (+ its entry in query_index)
+        keep = max(1, (limit - 4096) // per_query)  # (4096: room for the .npy headers)
+        idx = np.sort(np.random.default_rng(SEED).choice(n, size=keep, replace=False))
+        out = {name: v[idx] for name, v in out.items()}
+        out["query_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v))
 
 
 def main_flat(a):
@@ -280,6 +314,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the last timed step's results, read from the device buffers after the fence
+        # (a device-wide synchronise).  Not h_out: its copies run on torch's stream, which does not wait for the handle's own
+        # non-blocking search stream.
+        dump_outputs(a.dump_outputs, {"rowids": last[0].cpu().numpy(), "distances": last[1].cpu().numpy(), "counts": last[2].cpu().numpy()})
     st = ix.stats()
 
     # roofline of the dominant kernel (ADC scan): algorithmic code bytes per launch

@@ -513,11 +513,20 @@ def width_lines(a, torch, np, dev, shapes=((384, 24, 8), (3072, 192, 8), (768, 9
 
 # ------------------------------------------------------------------- concurrent host callers (no GIL) ----
 def build_loadgen():
-    """tests/tools/loadgen.cpp -> tests/tools/libloadgen.so (g++): N std::threads issuing single-query host-I/O calls."""
+    """tests/tools/loadgen.cpp -> tests/tools/libloadgen.so (g++): N std::threads issuing single-query host-I/O calls.
+    build() makes it; a checkout this process cannot write to gets a missing or stale library built in a private
+    temporary directory instead (removed at exit)."""
     import subprocess
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tests", "tools")
     src, lib = os.path.join(here, "loadgen.cpp"), os.path.join(here, "libloadgen.so")
     if not os.path.exists(lib) or os.path.getmtime(lib) < os.path.getmtime(src):
+        if not os.access(here, os.W_OK) or (os.path.exists(lib) and not os.access(lib, os.W_OK)):
+            import atexit
+            import shutil
+            import tempfile
+            tmp = tempfile.mkdtemp(prefix="loadgen-")
+            atexit.register(shutil.rmtree, tmp, True)
+            lib = os.path.join(tmp, "libloadgen.so")
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", lib], check=True)
     return lib
 

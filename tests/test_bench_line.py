@@ -76,3 +76,61 @@ def test_bench_with_gpus_2_without_a_launcher_says_what_to_run():
     assert r.returncode != 0
     msg = r.stderr + r.stdout
     assert "torch.distributed.run" in msg and "--nproc-per-node 2" in msg and "WORLD_SIZE" in msg, msg[-1500:]
+
+
+def test_bench_refuses_zero_timed_steps():
+    """`--steps` is the number of timed steps and `ms_per_step` is divided by it: zero is refused before any device work."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr, r.stderr[-1500:]
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_past_the_limit(tmp_path):
+    """--dump-outputs: integers become float64 (exact), floats stay float32; past the byte limit a seeded sample of the
+    queries is written, the same on every run, with the sampled positions beside it."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    ids = rng.integers(0, 100_000_000, size=(5000, 10), dtype=np.int64)
+    dist = rng.random((5000, 10), dtype=np.float32)
+    cnt = np.full(5000, 10, dtype=np.int32)
+    arrays = {"rowids": ids, "distances": dist, "counts": cnt}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in ("rowids", "distances", "counts")}
+    assert sorted(os.listdir(tmp_path / "all")) == ["counts.npy", "distances.npy", "rowids.npy"]
+    assert got["rowids"].dtype == np.float64 and (got["rowids"].astype(np.int64) == ids).all()
+    assert got["distances"].dtype == np.float32 and (got["distances"] == dist).all()
+    assert got["counts"].dtype == np.float64 and (got["counts"] == cnt).all()
+
+    limit = 200_000  # 5000 queries x 128 bytes = 640 000 bytes: sampled
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert total <= limit
+    idx = np.load(tmp_path / "s1" / "query_index.npy").astype(np.int64)
+    assert 1000 < len(idx) < 5000 and (np.diff(idx) > 0).all()
+    assert (np.load(tmp_path / "s1" / "rowids.npy").astype(np.int64) == ids[idx]).all()
+    assert (np.load(tmp_path / "s1" / "distances.npy") == dist[idx]).all()
+    for f in os.listdir(tmp_path / "s1"):
+        assert (np.load(tmp_path / "s1" / f) == np.load(tmp_path / "s2" / f)).all(), f
+
+
+def test_loadgen_is_built_outside_a_checkout_that_cannot_be_written(monkeypatch):
+    """The concurrent-callers leg loads tests/tools/libloadgen.so.  When the benchmark's user cannot write to the checkout and the
+    library is missing there, it is built in a private temporary directory rather than failing the whole benchmark."""
+    import ctypes as C
+    import shutil
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    tools = os.path.join(ROOT, "tests", "tools")
+    in_tree = os.path.join(tools, "libloadgen.so")
+    before = os.path.getmtime(in_tree) if os.path.exists(in_tree) else None
+    access, exists = os.access, os.path.exists
+    monkeypatch.setattr(os, "access", lambda p, mode, **kw: False if (mode & os.W_OK and str(p).startswith(tools)) else access(p, mode, **kw))
+    monkeypatch.setattr(os.path, "exists", lambda p: False if str(p) == in_tree else exists(p))
+    lib = legs.build_loadgen()
+    monkeypatch.undo()
+    assert not lib.startswith(tools) and os.path.exists(lib)
+    assert hasattr(C.CDLL(lib), "loadgen_run")
+    assert (os.path.getmtime(in_tree) if os.path.exists(in_tree) else None) == before  # the checkout was not written

@@ -213,6 +213,7 @@ def test_coalescing_queue_under_thread_sanitizer(tmp_path):
     window) compiled alone with ThreadSanitizer and driven by 48 CPU threads — a mutex-free stand-in for the device checks
     exclusive ownership, every call runs in exactly one batch, failed batches reach every caller they carried, and a lost
     wake-up would hang (timeout).  tests/test_gpu_concurrency.py runs the same header inside the library on the GPU."""
+    import platform
     import shutil
     import subprocess
     if not shutil.which("g++"):
@@ -226,7 +227,13 @@ def test_coalescing_queue_under_thread_sanitizer(tmp_path):
         pytest.skip("this toolchain has no ThreadSanitizer runtime")
     assert b.returncode == 0, b.stderr[-2000:]
     env = {k: v for k, v in os.environ.items() if k not in ("LD_PRELOAD", "ASAN_OPTIONS", "UBSAN_OPTIONS")}  # (scripts/asan_abi_tests.sh preloads ASan)
-    r = subprocess.run([exe, "48", "300"], capture_output=True, text=True, timeout=300, env=env)
+    # GCC's ThreadSanitizer runtime expects the classic x86-64 layout and aborts ("unexpected memory mapping") when a kernel with
+    # high-entropy ASLR (a large vm.mmap_rnd_bits) places the executable or a library elsewhere: run it without address
+    # randomisation (a personality flag of this one process)
+    norand = [shutil.which("setarch"), platform.machine(), "-R"] if shutil.which("setarch") else []
+    if norand and subprocess.run(norand + ["true"], capture_output=True).returncode != 0:
+        norand = []  # (not permitted here: run it as it is)
+    r = subprocess.run(norand + [exe, "48", "300"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and r.stdout.startswith("ok"), (r.stdout + r.stderr)[-3000:]
     assert "ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
 

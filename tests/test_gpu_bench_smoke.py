@@ -78,3 +78,29 @@ def test_sharded_bench_path_in_a_world_of_one():
         mg = d["multi_gpu"]
         assert mg["rccl_ranks"] == 1 and mg["sharded_equals_unsharded"] is True and mg["all_ranks_returned_the_same_results"] is True
         assert mg["coarse"].startswith("sharded" if extra else "replicated")
+
+
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's results; the inputs depend on the arguments only, so two runs with
+    the same arguments write the same arrays (what lets two builds be compared output for output).  `--steps` is the
+    number of timed steps the line reports."""
+    import numpy as np
+    pytest.importorskip("torch")
+    lines = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n-rows", "2000000", "--nlist", "512", "--batch", "256", "--steps", "3",
+               "--warmup", "1", "--secondary", "0", "--recall-rows", "0", "--recall2-rows", "0", "--cpu-seconds", "2",
+               "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.strip()][-1]))
+    for d in lines:
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert d["cpu_baseline"]["parity"]["rowids_bit_exact"]  # (the oracle checks queries of the same last batch)
+    assert sorted(os.listdir(tmp_path / "a")) == ["counts.npy", "distances.npy", "rowids.npy"]
+    got = {f: (np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in os.listdir(tmp_path / "a")}
+    assert got["rowids.npy"][0].shape == (256, 10) and got["rowids.npy"][0].dtype == np.float64
+    assert got["distances.npy"][0].dtype == np.float32 and got["counts.npy"][0].shape == (256,)
+    assert (got["counts.npy"][0] == 10).all() and (got["rowids.npy"][0] >= 0).all() and (got["rowids.npy"][0] < 2_000_000).all()
+    for f, (x, y) in got.items():
+        assert (x == y).all(), f
