@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MI355_ANN_ABI_VERSION 5u
+#define MI355_ANN_ABI_VERSION 6u
 
 /* ---- status codes (rust/lancedb/src/error.rs:55-145) -------------------- */
 enum {
@@ -96,7 +96,28 @@ enum {
      (mi355_shard_plan), concatenated in partition order — a rank never materialises the
      partitions of the others.  part_offsets stays the GLOBAL array (it defines the plan and
      the global positions); row_ids must then be given (identity ids would be global). */
-  MI355_INDEX_LOCAL_ARRAYS = 4u
+  MI355_INDEX_LOCAL_ARRAYS = 4u,
+  /* IVF_FLAT index (rust/lancedb/src/index.rs:80, index/vector.rs:170-210): the IVF partitions of an
+     IVF-PQ index without the PQ stage — a probed partition is scanned on its RAW rows with the exact
+     distance of mi355_flat_search.  The descriptor then has m = 0, nbits = 0, codebook = NULL,
+     codes = NULL (codes_layout is ignored) and REQUIRES raw_vectors ([n_rows, dim] per raw_dtype, in
+     index order).  mem = MI355_MEM_HOST: the column is copied to HBM at open; MI355_MEM_DEVICE: an
+     unsharded handle (or one with MI355_INDEX_LOCAL_ARRAYS) BORROWS the caller's device column, which
+     must outlive the handle — other shard handles copy their partitions out of it.  centroids,
+     part_offsets, row_ids, metric, sharding and part_owner keep their IVF-PQ meaning.
+     Not combinable with MI355_INDEX_GENERIC_SCAN (InvalidInput) nor MI355_INDEX_RAW_HOST_MAPPED
+     (NotSupported: a scan over PCIe).  On such a handle:
+       - probes are exactly those an IVF-PQ handle with the same centroids and metric picks (the same
+         coarse stage and selection, maximum_nprobes second pass included);
+       - inside the probed partitions the result is mi355_flat_search's over those rows: the exact
+         d-ascending chain of the caller's query (cosine NOT normalised first), [lower, upper), then
+         the prefilter, ordered by (distance, rowid), NaN dropped;
+       - refine_factor is accepted and changes nothing (the distances are already exact);
+       - mi355_index_attach_raw / detach_raw return InvalidInput (the raw column is the index);
+       - mi355_stats.scan_variant = MI355_SCAN_IVF_FLAT, code_bytes_scanned = dim * element size per
+         vector scanned;
+       - MI355_CFG_GRAPH is ignored (every call launches eagerly). */
+  MI355_INDEX_IVF_FLAT = 8u
 };
 
 /* layout of the PQ code block handed to mi355_index_open */
@@ -112,7 +133,7 @@ enum {
   MI355_CODES_PART_TRANSPOSED = 1
 };
 
-typedef struct mi355_index mi355_index; /* IVF-PQ index resident on one GPU */
+typedef struct mi355_index mi355_index; /* IVF-PQ or IVF_FLAT index resident on one GPU */
 typedef struct mi355_flat mi355_flat;   /* raw vector column resident on one GPU */
 
 /*
@@ -125,8 +146,8 @@ typedef struct mi355_index_desc {
   uint32_t struct_size; /* sizeof(mi355_index_desc), ABI guard */
   uint32_t dim;         /* vector dimension */
   uint32_t nlist;       /* IVF partitions (num_partitions) */
-  uint32_t m;           /* PQ sub-vectors (num_sub_vectors); dim % m == 0 */
-  uint32_t nbits;       /* PQ bits: 8, or 4 with even m (table/create_index.rs:96-101).
+  uint32_t m;           /* PQ sub-vectors (num_sub_vectors); dim % m == 0.  0 for MI355_INDEX_IVF_FLAT */
+  uint32_t nbits;       /* PQ bits: 8, or 4 with even m (table/create_index.rs:96-101); ignored by MI355_INDEX_IVF_FLAT.
                            4-BIT PARITY AGAINST lance-index IS UNKNOWN: the engine sums f32 table entries per row like the
                            8-bit path (and matches this repository's CPU restatement bit for bit); lance-index's 4-bit scan
                            is, to our knowledge, a SIMD-shuffle scan over a table QUANTISED to u8 [EXT], whose distances
@@ -144,7 +165,8 @@ typedef struct mi355_index_desc {
                                    NULL = identity (row i has _rowid i) */
   const void *raw_vectors;      /* optional [n_rows, dim] raw vectors in index
                                    order (refine stage, query.rs:1302-1332);
-                                   NULL = refine unavailable */
+                                   NULL = refine unavailable.  REQUIRED by
+                                   MI355_INDEX_IVF_FLAT: the rows it scans */
   uint32_t raw_dtype;           /* MI355_DTYPE_* of raw_vectors */
   int32_t device;               /* HIP device ordinal */
   /* Partition sharding over the GPUs of one node.  This
@@ -225,7 +247,7 @@ typedef struct mi355_stats {
   uint32_t n_queries;
   uint64_t partitions_probed;  /* sum over queries */
   uint64_t vectors_scanned;    /* sum over (query, partition) pairs */
-  uint64_t code_bytes_scanned; /* algorithmic bytes: m*nbits/8 per vector per query */
+  uint64_t code_bytes_scanned; /* algorithmic bytes: m*nbits/8 per vector per query (IVF_FLAT: dim * element size) */
   uint64_t work_items;         /* scan work items launched; for batches cut by rows on the device (up to 512 (query, partition) pairs
                                   that cannot fill the chip) the candidate-slot groups laid out for them: an upper bound of the items */
   float us_coarse;             /* per-stage device time; 0 unless profiling on */
@@ -235,7 +257,7 @@ typedef struct mi355_stats {
   float us_merge;
   float us_refine;
   float us_total;
-  uint32_t scan_variant;       /* which ADC kernel ran (MI355_SCAN_*) */
+  uint32_t scan_variant;       /* which scan kernel ran (MI355_SCAN_*) */
   uint32_t scan_launches;      /* timed launch sequences folded into us_* */
   uint32_t timed_out;          /* 1 = the device-side deadline of timeout_ms stopped the last call */
   uint32_t bad_probes;         /* mi355_search_probes: probe ids that are not partitions of this
@@ -250,13 +272,16 @@ enum {
   MI355_SCAN_AUTO = 0,
   MI355_SCAN_PAIR = 1,   /* generic: one workgroup per (query, partition slice),
                             [sub-quantiser][code] table, any m */
-  MI355_SCAN_SKEW = 2    /* production: pre-skewed code streams + [code][column]
+  MI355_SCAN_SKEW = 2,   /* production: pre-skewed code streams + [code][column]
                             table (bank-conflict-free gathers), partition-major
                             work queues per XCD; any m up to 768: a table holds
                             32 / 48 / 64 / 80 / 96 columns, other m <= 96 are padded
                             with zero columns, larger m are scanned in slabs of <= 96
                             columns (the row sum stays j-ascending); 4-bit codes are
                             expanded to one byte per sub-quantiser when packed */
+  MI355_SCAN_IVF_FLAT = 3 /* IVF_FLAT handles: one workgroup per (query, probed partition
+                            slice) computes the exact distance of every raw row of the
+                            slice (k_ivf_flat_scan) */
 };
 
 /* mi355_index_configure `profile` bits above the low byte */
@@ -301,7 +326,7 @@ int32_t mi355_index_set_stream(mi355_index *index, void *hip_stream);
 int32_t mi355_index_sync(mi355_index *index);
 /* tuning knobs: MI355_SCAN_* variant (AUTO = the one the index layout was
    packed for at open; a mismatching explicit choice is INVALID_INPUT), slice
-   length (rows per scan work item of the generic kernel, 0 = default) and
+   length (rows per scan work item of the generic and the IVF_FLAT kernel, 0 = default) and
    profiling (low byte of `profile`): 0 = counters only, 1 = also per-stage device
    times of the LAST search, 2 = counters and times ACCUMULATE over searches
    until the next configure().  Times come from hipEvents recorded on the search
@@ -315,7 +340,8 @@ int32_t mi355_index_configure(mi355_index *index, uint32_t scan_variant,
 /* Attach (or replace) the raw vector column of an open handle WITHOUT copying it: a DEVICE array
    [rows kept on this handle, dim] in the handle's local row order (= index order for an unsharded
    handle) that the caller keeps alive until detach / close.  For columns that should not exist
-   twice in HBM (100 M x 768 bf16 = 154 GB).  Detach restores the column given at open, if any. */
+   twice in HBM (100 M x 768 bf16 = 154 GB).  Detach restores the column given at open, if any.
+   Both return InvalidInput on an IVF_FLAT handle (its raw column is the index). */
 int32_t mi355_index_attach_raw(mi355_index *index, const void *raw_vectors, uint32_t raw_dtype);
 int32_t mi355_index_detach_raw(mi355_index *index);
 /* rows kept on this handle and how many partitions are non-empty here */
@@ -456,6 +482,10 @@ int32_t mi355_merge_topk(int32_t device, void *hip_stream,
  *   code_j(x)    = argmin_c chain_l2(r_j, codebook[j][c]) with r = x - c_partition
  *                  (dot: r = x, argmin_c 1 - chain_dot(x_j, codebook[j][c])), ties to the lower c
  *   order        = rows sorted by (partition, source row): stable
+ * Assign-only mode (population of an IVF_FLAT index, MI355_INDEX_IVF_FLAT): m = 0,
+ * codebook = NULL and out_codes = NULL.  part_offsets, order and assign are those of the PQ
+ * call with the same centroids and metric; nothing is encoded (nbits is ignored).  Any other
+ * call with m = 0 is InvalidInput.
  */
 typedef struct mi355_encode_desc {
   uint32_t struct_size;

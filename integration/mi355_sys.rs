@@ -6,8 +6,8 @@
 #![allow(non_camel_case_types, non_upper_case_globals, dead_code)]
 use core::ffi::{c_char, c_void};
 
-// ---- constants (48)
-pub const MI355_ANN_ABI_VERSION: u32 = 5;
+// ---- constants (50)
+pub const MI355_ANN_ABI_VERSION: u32 = 6;
 pub const MI355_COMM_ID_BYTES: usize = 128;
 pub const MI355_MAX_RANKS: usize = 64;
 pub const MI355_OK: i32 = 0;
@@ -31,6 +31,7 @@ pub const MI355_APPROX_ACCURATE: u32 = 3;
 pub const MI355_INDEX_GENERIC_SCAN: u32 = 1;
 pub const MI355_INDEX_RAW_HOST_MAPPED: u32 = 2;
 pub const MI355_INDEX_LOCAL_ARRAYS: u32 = 4;
+pub const MI355_INDEX_IVF_FLAT: u32 = 8;
 pub const MI355_CODES_ROW_MAJOR: u32 = 0;
 pub const MI355_CODES_PART_TRANSPOSED: u32 = 1;
 pub const MI355_FILTER_NONE: u32 = 0;
@@ -39,6 +40,7 @@ pub const MI355_FILTER_BLOCK: u32 = 2;
 pub const MI355_SCAN_AUTO: u32 = 0;
 pub const MI355_SCAN_PAIR: u32 = 1;
 pub const MI355_SCAN_SKEW: u32 = 2;
+pub const MI355_SCAN_IVF_FLAT: u32 = 3;
 pub const MI355_PROFILE_MASK: u32 = 255;
 pub const MI355_CFG_GRAPH: u32 = 256;
 pub const MI355_CFG_COALESCE: u32 = 512;

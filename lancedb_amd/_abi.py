@@ -6,7 +6,7 @@ exactly; `struct_size` guards against drift at run time.
 """
 import ctypes as C
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 OK = 0
 ERR_INVALID_INPUT = 1
@@ -32,6 +32,7 @@ CODES_PART_TRANSPOSED = 1
 SCAN_AUTO = 0
 SCAN_PAIR = 1
 SCAN_SKEW = 2
+SCAN_IVF_FLAT = 3
 
 FILTER_NONE = 0
 FILTER_ALLOW = 1
@@ -46,6 +47,7 @@ APPROX_NAMES = {"fast": APPROX_FAST, "normal": APPROX_NORMAL, "accurate": APPROX
 INDEX_GENERIC_SCAN = 1
 INDEX_RAW_HOST_MAPPED = 2
 INDEX_LOCAL_ARRAYS = 4
+INDEX_IVF_FLAT = 8
 
 PROFILE_MASK = 0xFF
 CFG_GRAPH = 0x100

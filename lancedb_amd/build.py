@@ -1,4 +1,4 @@
-"""Host side of `Table.create_index(Index::IvfPq(..))` for this engine: the
+"""Host side of `Table.create_index(Index::IvfPq(..))` / `Index::IvfFlat(..)` for this engine: the
 reference's builder parameters (rust/lancedb/src/index/vector.rs:61-119,
 :306-319; mapping to IvfBuildParams / PQBuildParams in
 rust/lancedb/src/table/create_index.rs:68-102, :283-303) driving the GPU
@@ -10,7 +10,7 @@ import math
 
 import numpy as np
 
-from .index import IvfPqIndex, ivf_residuals, ivfpq_encode, kmeans_train, pq_train
+from .index import IvfFlatIndex, IvfPqIndex, ivf_flat_assign, ivf_residuals, ivfpq_encode, kmeans_train, pq_train
 
 
 DEFAULT_PARTITION_SIZE = 8192  # rows per partition of IvfBuildParams::default() [EXT], pinned by
@@ -108,3 +108,39 @@ class IvfPqBuilder:
         ids = order.astype(np.uint64) if row_ids is None else np.asarray(row_ids, dtype=np.uint64)[order]
         return IvfPqIndex(centroids, codebook, po, codes, ids, raw_vectors=x[order] if keep_vectors else None,
                           metric=self.distance_type, nbits=self.num_bits)
+
+
+class IvfFlatBuilder:
+    """Mirror of `IvfFlatIndexBuilder` (index/vector.rs:170-210; python/python/lancedb/index.py:536 `IvfFlat`):
+    distance_type (default l2), num_partitions (None: rows / 8192, see num_partitions_for), target_partition_size,
+    sample_rate (256) and max_iterations (50).  Training is IvfPqBuilder's IVF stage (kmeans_train on a sample of
+    sample_rate * num_partitions rows); population is the assign-only mode of mi355_ivfpq_encode."""
+
+    def __init__(self, distance_type="l2", num_partitions=None, target_partition_size=None, sample_rate=256,
+                 max_iterations=50, seed=0):
+        self.distance_type, self.num_partitions, self.target_partition_size = distance_type, num_partitions, target_partition_size
+        self.sample_rate, self.max_iterations, self.seed = sample_rate, max_iterations, seed
+
+    def train(self, vectors):
+        """-> centroids [nlist, dim] (the same draws and iterations as IvfPqBuilder.train's IVF stage)."""
+        x = np.ascontiguousarray(vectors, dtype=np.float32)
+        n = x.shape[0]
+        nlist = num_partitions_for(n, self.num_partitions, self.target_partition_size)
+        if n < nlist:
+            raise ValueError(f"not enough rows ({n}) to train {nlist} partitions")
+        rng = np.random.default_rng(self.seed)
+        ivf_sample = IvfPqBuilder._sample(self, x, self.sample_rate * nlist, rng)
+        init = ivf_sample[np.sort(rng.choice(ivf_sample.shape[0], size=nlist, replace=False))]
+        if self.distance_type == "cosine":  # the trainer normalises the rows; seed it with normalised rows too
+            init = init / np.maximum(np.linalg.norm(init, axis=1, keepdims=True), np.float32(1e-30))
+        centroids, _ = kmeans_train(ivf_sample, init, metric=self.distance_type, iters=self.max_iterations)
+        return centroids
+
+    def build(self, vectors, row_ids=None):
+        """Train, assign every row and open the device index over the rows in partition order."""
+        x = np.ascontiguousarray(vectors, dtype=np.float32)
+        centroids = self.train(x)
+        po, order = ivf_flat_assign(x, centroids, metric=self.distance_type)
+        order = order.astype(np.int64)
+        ids = order.astype(np.uint64) if row_ids is None else np.asarray(row_ids, dtype=np.uint64)[order]
+        return IvfFlatIndex(centroids, po, x[order], ids, metric=self.distance_type)

@@ -55,16 +55,21 @@ extern "C" int32_t mi355_ivfpq_encode(const mi355_encode_desc* d, const float* v
   if (d->struct_size != sizeof(mi355_encode_desc))
     return fail(MI355_ERR_INVALID_INPUT, "mi355_encode_desc.struct_size %u != %zu (ABI mismatch)", d->struct_size,
                 sizeof(mi355_encode_desc));
-  if (d->dim == 0 || d->nlist == 0 || d->m == 0) return fail(MI355_ERR_INVALID_INPUT, "dim, nlist and m must be > 0");
+  // assign-only (IVF_FLAT population): partitions and order, no codes
+  const bool assign_only = d->m == 0 && !d->codebook && !out_codes;
+  if (d->dim == 0 || d->nlist == 0 || (d->m == 0 && !assign_only))
+    return fail(MI355_ERR_INVALID_INPUT, "dim, nlist and m must be > 0 (m = 0 only with codebook = NULL and out_codes = NULL: assign-only)");
+  if (!assign_only) {
   if (d->dim % d->m) return fail(MI355_ERR_INVALID_INPUT, "dim %u is not a multiple of m %u", d->dim, d->m);
   if (d->nbits != 8 && d->nbits != 4) return fail(MI355_ERR_INVALID_INPUT, "num_bits must be 4 or 8, got %u", d->nbits);
   if (d->nbits == 4 && d->m % 2) return fail(MI355_ERR_INVALID_INPUT, "num_sub_vectors must be even when num_bits is 4, got %u", d->m);
+  }
   if (d->metric > MI355_METRIC_DOT || d->mem > MI355_MEM_DEVICE) return fail(MI355_ERR_INVALID_INPUT, "bad metric / mem enum");
-  if (!d->centroids || !d->codebook || !out_part_offsets) return fail(MI355_ERR_INVALID_INPUT, "NULL buffer");
-  if (n_rows && (!vectors || !out_codes || !out_order)) return fail(MI355_ERR_INVALID_INPUT, "NULL buffer");
-  const uint32_t dim = d->dim, nlist = d->nlist, m = d->m, dsub = dim / m;
-  const uint32_t ks = 1u << d->nbits, mb = m * d->nbits / 8;  // codebook entries, code bytes per row
-  const uint32_t jt = d->nbits == 4 ? 2 : (m % 4 == 0) ? 4 : 1;
+  if (!d->centroids || (!assign_only && !d->codebook) || !out_part_offsets) return fail(MI355_ERR_INVALID_INPUT, "NULL buffer");
+  if (n_rows && (!vectors || (!assign_only && !out_codes) || !out_order)) return fail(MI355_ERR_INVALID_INPUT, "NULL buffer");
+  const uint32_t dim = d->dim, nlist = d->nlist, m = d->m, dsub = m ? dim / m : 0u, nbits = assign_only ? 8u : d->nbits;
+  const uint32_t ks = 1u << nbits, mb = m * nbits / 8;  // codebook entries, code bytes per row
+  const uint32_t jt = nbits == 4 ? 2 : (m % 4 == 0) ? 4 : 1;
   if ((size_t)jt * ks * dsub * 4 > 150u * 1024)
     return fail(MI355_ERR_NOT_SUPPORTED, "dim / m = %u: the codebook slices do not fit LDS", dsub);
   if ((size_t)dim * 16 > 150u * 1024) return fail(MI355_ERR_NOT_SUPPORTED, "dim %u too large", dim);
@@ -83,7 +88,7 @@ extern "C" int32_t mi355_ivfpq_encode(const mi355_encode_desc* d, const float* v
   chunk = std::min<uint64_t>(chunk, (n_rows + 255) & ~(uint64_t)255);
 
   ST_TRY(w.cen.ensure(sizeof(float) * (size_t)nlist * dim));
-  ST_TRY(w.cb.ensure(sizeof(float) * (size_t)m * ks * dsub));
+  if (m) ST_TRY(w.cb.ensure(sizeof(float) * (size_t)m * ks * dsub));
   ST_TRY(w.cn.ensure(sizeof(float) * nlist));
   ST_TRY(w.qp.ensure(sizeof(float) * chunk * dim));
   ST_TRY(w.qq.ensure(sizeof(float) * chunk));
@@ -97,14 +102,15 @@ extern "C" int32_t mi355_ivfpq_encode(const mi355_encode_desc* d, const float* v
     ST_TRY(w.order.ensure(sizeof(uint64_t) * n_rows));
   }
   HIP_TRY(copy_in(w.cen.p, d->centroids, sizeof(float) * (size_t)nlist * dim, d->mem, st));
-  HIP_TRY(copy_in(w.cb.p, d->codebook, sizeof(float) * (size_t)m * ks * dsub, d->mem, st));
+  if (m) HIP_TRY(copy_in(w.cb.p, d->codebook, sizeof(float) * (size_t)m * ks * dsub, d->mem, st));
   hipLaunchKernelGGL(k_centroid_norms, dim3((nlist + 63) / 64), dim3(64), 0, st, w.cen.as<float>(), nlist, dim,
                      w.cn.as<float>());
   HIP_TRY(hipMemsetAsync(w.hist.p, 0, sizeof(uint32_t) * nlist, st));
 
   // ---- pass A: partition + codes of every row, in source order
   const size_t enc_lds = (size_t)jt * ks * dsub * 4;
-  if (d->nbits == 4)
+  if (assign_only) {
+  } else if (nbits == 4)
     HIP_TRY(hipFuncSetAttribute((const void*)k_encode_rows<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds));
   else if (jt == 4)
     HIP_TRY(hipFuncSetAttribute((const void*)k_encode_rows<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds));
@@ -126,7 +132,8 @@ extern "C" int32_t mi355_ivfpq_encode(const mi355_encode_desc* d, const float* v
                        w.assign.as<uint32_t>() + r0, w.hist.as<uint32_t>());
     EncodeArgs ea{w.qp.as<float>(), r0, n, w.assign.as<uint32_t>(), w.cen.as<float>(), w.cb.as<float>(),
                   dim, m, dsub, d->metric, mb, w.codes_src.as<uint8_t>()};
-    if (d->nbits == 4)
+    if (assign_only) {
+    } else if (nbits == 4)
       hipLaunchKernelGGL((k_encode_rows<2, 4>), dim3((n + 255) / 256, m / 2), dim3(256), enc_lds, st, ea);
     else if (jt == 4)
       hipLaunchKernelGGL((k_encode_rows<4, 8>), dim3((n + 255) / 256, m / 4), dim3(256), enc_lds, st, ea);
@@ -157,7 +164,7 @@ extern "C" int32_t mi355_ivfpq_encode(const mi355_encode_desc* d, const float* v
 
   // ---- pass C: code rows into index order
   uint8_t* d_codes = host ? w.codes_dst.as<uint8_t>() : out_codes;
-  {
+  if (!assign_only) {
     const uint32_t pw = (mb % 4 == 0) ? 4 : 1;  // bytes per thread
     const uint64_t items = n_rows * (mb / pw);
     const uint64_t blocks = (items + 255) / 256;
@@ -171,7 +178,7 @@ extern "C" int32_t mi355_ivfpq_encode(const mi355_encode_desc* d, const float* v
     HIP_TRY(hipGetLastError());
   }
   if (host) {
-    HIP_TRY(hipMemcpyAsync(out_codes, d_codes, (size_t)n_rows * mb, hipMemcpyDeviceToHost, st));
+    if (!assign_only) HIP_TRY(hipMemcpyAsync(out_codes, d_codes, (size_t)n_rows * mb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_order, d_order, sizeof(uint64_t) * n_rows, hipMemcpyDeviceToHost, st));
   }
   if (out_assign)

@@ -643,6 +643,8 @@ extern "C" int32_t mi355_search_sharded(mi355_index* ix, mi355_comm* c, const fl
                                         float* out_dist, uint32_t* out_counts) try {
   if (!c) return fail(MI355_ERR_INVALID_INPUT, "comm is NULL");
   if (flags & ~(uint32_t)(MI355_SHARD_COARSE | MI355_SHARD_NO_OVERLAP)) return fail(MI355_ERR_INVALID_INPUT, "unknown flags 0x%x", flags);
+  mi355_search_params p_flat;
+  p = ivf_flat_params(ix, p, &p_flat);  // (IVF_FLAT: refine_factor changes nothing)
   SearchShape sh;
   ST_TRY(check_search(ix, queries, n_queries, p, nullptr, 0, out_rowids, out_dist, out_counts, &sh, true));
   if (ix->shard_count != c->world || ix->shard_rank != c->rank)

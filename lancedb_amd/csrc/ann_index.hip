@@ -9,6 +9,7 @@
 // plan.  Handle lifecycle: ann_index_open.hip; call driver (request checks, coalescing queue, graph cache, host I/O):
 // ann_index_search.hip.
 #include "ann_internal.h"
+#include "kernels_ivf_flat.h"
 #include "kernels_ivfpq.h"
 #include "kernels_skew.h"
 
@@ -60,7 +61,8 @@ extern "C" int32_t mi355_last_stats(mi355_index* ix, mi355_stats* out) try {
   DevCtl h_ctl;
   HIP_TRY(hipMemcpy(&h_ctl, ix->w_ctl.p, sizeof(DevCtl), hipMemcpyDeviceToHost));
   ix->stats.vectors_scanned = h_ctl.rows_scanned;
-  ix->stats.code_bytes_scanned = h_ctl.rows_scanned * ix->mb;  // algorithmic bytes: m * nbits / 8 per vector
+  // algorithmic bytes: m * nbits / 8 per vector (IVF_FLAT: the raw row)
+  ix->stats.code_bytes_scanned = h_ctl.rows_scanned * (ix->ivf_flat ? (uint64_t)ix->dim * dtype_size(ix->raw_dtype) : (uint64_t)ix->mb);
   ix->stats.timed_out = h_ctl.timed_out;
   ix->stats.bad_probes = h_ctl.bad_probes;
   *out = ix->stats;
@@ -195,6 +197,7 @@ int32_t run_ivfpq(mi355_index* ix, const float* d_q, uint32_t nq, const SearchPl
   const int kpl_kk = kpl_for(pl.kk), kpl_k = kpl_for(pl.k);
 
   const bool skew = ix->layout == MI355_SCAN_SKEW;
+  const bool ivf_flat = ix->layout == MI355_SCAN_IVF_FLAT;
   // tuning (dev knobs; defaults chosen from the index shape)
   uint32_t nt = dev_knob("MI355_SCAN_THREADS", 0), vpt = dev_knob("MI355_SCAN_VPT", 0);
   if (!nt) nt = pl.kk > 64 ? 256 : ix->max_len >= 8192 ? 1024 : ix->max_len >= 2048 ? 512 : 256;
@@ -214,6 +217,17 @@ int32_t run_ivfpq(mi355_index* ix, const float* d_q, uint32_t nq, const SearchPl
     slice = std::max((ix->max_len + want - 1) / want, nt * vpt);
   }
   slice = (slice + 15u) & ~15u;
+  if (ivf_flat) {
+    // IVF_FLAT: whole partitions once the batch gives every CU ~8 work items; smaller batches cut the partitions into
+    // slices of >= 1024 rows (each slice re-reads the query and reduces its own lists).  Slices are whole 256-row sweeps.
+    slice = ix->slice_rows;
+    if (!slice) {
+      const uint64_t pairs = std::max<uint64_t>((uint64_t)nq * nprobe, 1);
+      const uint32_t want = pairs >= 2048 ? 1u : (uint32_t)((2048 + pairs - 1) / pairs);
+      slice = std::max((ix->max_len + want - 1) / want, 1024u);
+    }
+    slice = (std::max(slice, 1u) + 255u) & ~255u;
+  }
   // the production scan slices by tile positions instead (SkewArgs::n_slices): only when the batch cannot
   // give every CU a work item, and never below ~2 k rows per slice (each slice rebuilds the distance table)
   uint32_t sk_slices = 1;
@@ -561,6 +575,22 @@ int32_t run_ivfpq(mi355_index* ix, const float* d_q, uint32_t nq, const SearchPl
         ST_TRY(launch_scan_skew_lat(ka, ix->sk_M, n_blocks, (uint64_t)n * nprobe * n_slices, pl.kk, st));
       else
         ST_TRY(launch_scan_skew(ka, ix->sk_M, ix->sk_slabbed, n_blocks, (uint64_t)n * nprobe * n_slices, pl.kk, st));
+    } else if (ivf_flat) {
+      if (prof) HIP_TRY(hipEventRecord(es.ev[6], st));
+      IvfFlatArgs fa;
+      fa.ix = view;
+      fa.q = q;  // the caller's queries: the exact distance of the flat search (cosine not normalised first)
+      fa.probes = ix->w_probes.as<uint32_t>();
+      fa.nprobe = nprobe;
+      fa.slice_rows = slice;
+      fa.n_slices = n_slices;
+      fa.kk = pl.kk;
+      fa.range = pl.range;
+      fa.filter = pl.filter;
+      fa.cand = ix->w_cand.as<Cand>();
+      fa.ctl = d_ctl;
+      fa.act = act;
+      ST_TRY(launch_scan_ivf_flat(fa, n, st));
     } else {
       if (prof) HIP_TRY(hipEventRecord(es.ev[6], st));
       ScanArgs sa;

@@ -81,7 +81,7 @@ IndexView make_view(const mi355_index* ix) {
   v.lrow0 = ix->lrow0.as<uint32_t>();
   v.grow0 = ix->grow0.as<uint64_t>();
   v.row_ids = ix->has_row_ids ? ix->row_ids.as<uint64_t>() : nullptr;
-  v.raw = ix->has_raw ? (ix->raw_mapped_dev ? ix->raw_mapped_dev : ix->raw.p) : nullptr;
+  v.raw = ix->has_raw ? (ix->raw_mapped_dev ? ix->raw_mapped_dev : ix->raw_borrowed ? ix->raw_borrowed : ix->raw.p) : nullptr;
   v.raw_dtype = ix->raw_dtype;
   v.raw_by_global = (ix->raw_mapped_dev && !ix->local_arrays) ? 1u : 0u;
   if (ix->raw_attached) {  // a borrowed device column in local row order takes precedence
@@ -97,6 +97,19 @@ static int32_t validate_index_desc(const mi355_index_desc* d) {
   if (d->struct_size != sizeof(mi355_index_desc))
     return fail(MI355_ERR_INVALID_INPUT, "mi355_index_desc.struct_size %u != %zu (ABI mismatch)",
                 d->struct_size, sizeof(mi355_index_desc));
+  const bool ivf_flat = (d->flags & MI355_INDEX_IVF_FLAT) != 0;
+  if (ivf_flat) {  // IVF_FLAT (index.rs:80): no PQ stage, the raw rows are the index
+    if (d->m != 0 || d->codebook || d->codes)
+      return fail(MI355_ERR_INVALID_INPUT, "MI355_INDEX_IVF_FLAT takes no PQ stage: m must be 0, codebook and codes NULL");
+    if (!d->raw_vectors) return fail(MI355_ERR_INVALID_INPUT, "MI355_INDEX_IVF_FLAT needs raw_vectors (the rows it scans)");
+    if (d->flags & MI355_INDEX_GENERIC_SCAN)
+      return fail(MI355_ERR_INVALID_INPUT, "MI355_INDEX_IVF_FLAT cannot be combined with MI355_INDEX_GENERIC_SCAN");
+    if (d->flags & ~(uint32_t)(MI355_INDEX_RAW_HOST_MAPPED | MI355_INDEX_LOCAL_ARRAYS | MI355_INDEX_IVF_FLAT))
+      return fail(MI355_ERR_INVALID_INPUT, "unknown index flags 0x%x", d->flags);
+    if (d->flags & MI355_INDEX_RAW_HOST_MAPPED)
+      return fail(MI355_ERR_NOT_SUPPORTED, "MI355_INDEX_IVF_FLAT scans its raw column in HBM: MI355_INDEX_RAW_HOST_MAPPED is not supported");
+    if (d->dim == 0 || d->nlist == 0) return fail(MI355_ERR_INVALID_INPUT, "dim and nlist must be > 0");
+  } else {
   if (d->nbits != 8 && d->nbits != 4) return fail(MI355_ERR_INVALID_INPUT, "num_bits must be 4 or 8, got %u", d->nbits);
   if (d->dim == 0 || d->nlist == 0 || d->m == 0)
     return fail(MI355_ERR_INVALID_INPUT, "dim, nlist and m must be > 0");
@@ -107,18 +120,21 @@ static int32_t validate_index_desc(const mi355_index_desc* d) {
     return fail(MI355_ERR_INVALID_INPUT, "num_sub_vectors must be even when num_bits is 4, got %u", d->m);
   if (d->flags & ~(uint32_t)(MI355_INDEX_GENERIC_SCAN | MI355_INDEX_RAW_HOST_MAPPED | MI355_INDEX_LOCAL_ARRAYS))
     return fail(MI355_ERR_INVALID_INPUT, "unknown index flags 0x%x", d->flags);
+  }
   if ((d->flags & MI355_INDEX_LOCAL_ARRAYS) && d->n_rows && !d->row_ids)
     return fail(MI355_ERR_INVALID_INPUT, "MI355_INDEX_LOCAL_ARRAYS needs row_ids (identity ids would be global positions)");
   if ((d->flags & MI355_INDEX_RAW_HOST_MAPPED) && (d->mem != MI355_MEM_HOST || !d->raw_vectors))
     return fail(MI355_ERR_INVALID_INPUT, "MI355_INDEX_RAW_HOST_MAPPED needs host raw_vectors (mem = MI355_MEM_HOST)");
   if (d->metric > MI355_METRIC_DOT)
     return fail(MI355_ERR_INVALID_INPUT, "unknown metric %u", d->metric);
-  if (d->mem > MI355_MEM_DEVICE || d->codes_layout > MI355_CODES_PART_TRANSPOSED ||
+  if (d->mem > MI355_MEM_DEVICE || (!ivf_flat && d->codes_layout > MI355_CODES_PART_TRANSPOSED) ||
       d->raw_dtype > MI355_DTYPE_F16)
     return fail(MI355_ERR_INVALID_INPUT, "bad mem / codes_layout / raw_dtype enum");
-  if (!d->centroids || !d->codebook || !d->part_offsets)
+  if (ivf_flat && (!d->centroids || !d->part_offsets))
+    return fail(MI355_ERR_INVALID_INPUT, "centroids and part_offsets are required");
+  if (!ivf_flat && (!d->centroids || !d->codebook || !d->part_offsets))
     return fail(MI355_ERR_INVALID_INPUT, "centroids, codebook and part_offsets are required");
-  if (d->n_rows && !d->codes) return fail(MI355_ERR_INVALID_INPUT, "codes is NULL");
+  if (!ivf_flat && d->n_rows && !d->codes) return fail(MI355_ERR_INVALID_INPUT, "codes is NULL");
   if (d->part_offsets[0] != 0 || d->part_offsets[d->nlist] != d->n_rows)
     return fail(MI355_ERR_INVALID_INPUT, "part_offsets must run from 0 to n_rows");
   for (uint32_t p = 0; p < d->nlist; ++p) {
@@ -136,7 +152,7 @@ static int32_t validate_index_desc(const mi355_index_desc* d) {
         return fail(MI355_ERR_INVALID_INPUT, "part_owner[%u] = %u is not a shard of %u", p, d->part_owner[p], d->shard_count);
   // an 8-bit distance table larger than the LDS keeps its tail in global memory (k_scan_pair SPILL);
   // what cannot work is a residual + candidate lists that leave no room for any table
-  if (scan_pair_m_lds(d->m, d->nbits, d->dim) == 0)
+  if (!ivf_flat && scan_pair_m_lds(d->m, d->nbits, d->dim) == 0)
     return fail(MI355_ERR_NOT_SUPPORTED, "dim %u / %u sub-vectors x %u entries do not fit the 160 KiB LDS", d->dim,
                 d->m, 1u << d->nbits);
   return MI355_OK;
@@ -179,10 +195,11 @@ static int32_t index_open_impl(const mi355_index_desc* d, mi355_index* ix) {
   ix->device = d->device;
   ix->dim = d->dim;
   ix->nlist = d->nlist;
-  ix->m = d->m;
-  ix->dsub = d->dim / d->m;
-  ix->nbits = d->nbits;
-  ix->mb = d->m * d->nbits / 8;
+  ix->ivf_flat = (d->flags & MI355_INDEX_IVF_FLAT) != 0;
+  ix->m = ix->ivf_flat ? 0u : d->m;
+  ix->dsub = ix->ivf_flat ? 0u : d->dim / d->m;
+  ix->nbits = ix->ivf_flat ? 0u : d->nbits;
+  ix->mb = ix->m * ix->nbits / 8;
   ix->metric = d->metric;
   ix->local_arrays = (d->flags & MI355_INDEX_LOCAL_ARRAYS) != 0;
   ix->shard_count = d->shard_count > 1 ? d->shard_count : 1;
@@ -190,7 +207,7 @@ static int32_t index_open_impl(const mi355_index_desc* d, mi355_index* ix) {
   HIP_TRY(hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking));
   ix->stream = ix->own_stream;
   hipStream_t st = ix->stream;
-  const uint32_t nlist = d->nlist, m = d->m, mb = ix->mb, cb_entries = 1u << d->nbits;
+  const uint32_t nlist = d->nlist, m = ix->m, mb = ix->mb, cb_entries = 1u << ix->nbits;
   for (DevBuf* b : {&ix->w_q, &ix->w_qp, &ix->w_qq, &ix->w_coarse, &ix->w_probes, &ix->w_cand, &ix->w_ids, &ix->w_dist,
                     &ix->w_pos, &ix->w_cnt, &ix->w_ids2, &ix->w_dist2, &ix->w_cnt2, &ix->w_cand2, &ix->items, &ix->qthr, &ix->w_ccnt,
                     &ix->w_filter, &ix->w_probes64, &ix->w_spill, &ix->w_partial, &ix->w_cand2b, &ix->w_cnt2b, &ix->w_lutres, &ix->w_lutimg})
@@ -212,8 +229,8 @@ static int32_t index_open_impl(const mi355_index_desc* d, mi355_index* ix) {
     // columns) whose work item fits the LDS: the 256 x 128-dword table + one slab's residual (the whole row's when
     // there is one slab) + the candidate lists of eight waves; a thread stages at most four residual elements.
     SkewShape shp{};
-    ix->layout = MI355_SCAN_PAIR;
-    if (!force_pair && sk_shape(m, &shp)) {  // (4-bit codes are expanded to one byte per column at pack time)
+    ix->layout = ix->ivf_flat ? MI355_SCAN_IVF_FLAT : MI355_SCAN_PAIR;
+    if (!ix->ivf_flat && !force_pair && sk_shape(m, &shp)) {  // (4-bit codes are expanded to one byte per column at pack time)
       const uint32_t res_floats = shp.n_slabs > 1 ? shp.M * ix->dsub : d->dim;
       // what the packed streams cost against the source rows: padding to a 32-column tile, nibbles expanded to bytes
       // (m = 8 at 4 bits streams 8 x its code bytes, m = 1 thirty-two times) — past 8 x the generic layout is the
@@ -230,7 +247,7 @@ static int32_t index_open_impl(const mi355_index_desc* d, mi355_index* ix) {
     }
   }
   const bool skew = ix->layout == MI355_SCAN_SKEW;
-  ix->lut_img_ok = lut_images_shape_ok(ix);  // batch-level distance tables (kernels_lut.h) for this shape
+  ix->lut_img_ok = !ix->ivf_flat && lut_images_shape_ok(ix);  // batch-level distance tables (kernels_lut.h) for this shape
   const bool local_arrays = (d->flags & MI355_INDEX_LOCAL_ARRAYS) != 0;
   for (uint32_t p = 0; p < nlist; ++p) {
     uint64_t len = d->part_offsets[p + 1] - d->part_offsets[p];
@@ -259,14 +276,14 @@ static int32_t index_open_impl(const mi355_index_desc* d, mi355_index* ix) {
   // -- small tables
   ST_TRY(ix->centroids.ensure(sizeof(float) * (size_t)nlist * d->dim));
   ST_TRY(ix->cnorm.ensure(sizeof(float) * nlist));
-  ST_TRY(ix->codebook.ensure(sizeof(float) * (size_t)m * cb_entries * ix->dsub));
+  if (m) ST_TRY(ix->codebook.ensure(sizeof(float) * (size_t)m * cb_entries * ix->dsub));
   ST_TRY(ix->code_off.ensure(sizeof(uint64_t) * nlist));
   ST_TRY(ix->plen.ensure(sizeof(uint32_t) * nlist));
   ST_TRY(ix->pstride.ensure(sizeof(uint32_t) * nlist));
   ST_TRY(ix->lrow0.ensure(sizeof(uint32_t) * nlist));
   ST_TRY(ix->grow0.ensure(sizeof(uint64_t) * nlist));
   HIP_TRY(copy_in(ix->centroids.p, d->centroids, sizeof(float) * (size_t)nlist * d->dim, d->mem, st));
-  HIP_TRY(copy_in(ix->codebook.p, d->codebook, sizeof(float) * (size_t)m * cb_entries * ix->dsub, d->mem, st));
+  if (m) HIP_TRY(copy_in(ix->codebook.p, d->codebook, sizeof(float) * (size_t)m * cb_entries * ix->dsub, d->mem, st));
   HIP_TRY(hipMemcpyAsync(ix->code_off.p, code_off.data(), sizeof(uint64_t) * nlist, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(ix->plen.p, plen.data(), sizeof(uint32_t) * nlist, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(ix->pstride.p, pstride.data(), sizeof(uint32_t) * nlist, hipMemcpyHostToDevice, st));
@@ -278,7 +295,7 @@ static int32_t index_open_impl(const mi355_index_desc* d, mi355_index* ix) {
 
   // -- PQ codes: stage (host source) and re-pack into [m][pstride] blocks
   ST_TRY(ix->codes.ensure(bytes + 64));
-  if (rows) {
+  if (rows && !ix->ivf_flat) {
     const size_t STAGE = (size_t)dev_knob("MI355_STAGE_MB", 256) << 20;
     ScratchBuf stage, d_srcoff, d_pids;
     std::vector<uint64_t> srcoff;
@@ -456,6 +473,12 @@ static int32_t index_open_impl(const mi355_index_desc* d, mi355_index* ix) {
     ix->has_raw = true;
     ix->raw_dtype = d->raw_dtype;
     ix->raw_is_host = true;
+  } else if (ix->ivf_flat && d->mem == MI355_MEM_DEVICE && (ix->shard_count == 1 || local_arrays)) {
+    // IVF_FLAT over a device column already in this handle's row order: scanned where it is (the column is the index;
+    // a second copy of 10 M x 768 f32 would be another 31 GB of HBM)
+    ix->raw_borrowed = d->raw_vectors;
+    ix->has_raw = true;
+    ix->raw_dtype = d->raw_dtype;
   } else if (d->raw_vectors) {
     ST_TRY(gather_rows(ix->raw, d->raw_vectors, dtype_size(d->raw_dtype) * d->dim));
     ix->has_raw = true;
@@ -529,7 +552,7 @@ extern "C" int32_t mi355_index_sync(mi355_index* ix) try {
 extern "C" int32_t mi355_index_configure(mi355_index* ix, uint32_t scan_variant,
                                          uint32_t slice_rows, uint32_t profile) try {
   if (!ix) return fail(MI355_ERR_INVALID_INPUT, "index is NULL");
-  if (scan_variant > MI355_SCAN_SKEW) return fail(MI355_ERR_INVALID_INPUT, "unknown scan variant");
+  if (scan_variant > MI355_SCAN_IVF_FLAT) return fail(MI355_ERR_INVALID_INPUT, "unknown scan variant");
   if ((profile & MI355_PROFILE_MASK) > 2 ||
       (profile & ~(uint32_t)(MI355_PROFILE_MASK | MI355_CFG_GRAPH | MI355_CFG_COALESCE | MI355_CFG_DEFER_REFINE | MI355_CFG_LUT_INLINE)))
     return fail(MI355_ERR_INVALID_INPUT, "unknown profile / mode bits 0x%x", profile);
@@ -561,6 +584,7 @@ extern "C" int32_t mi355_index_configure(mi355_index* ix, uint32_t scan_variant,
 
 extern "C" int32_t mi355_index_attach_raw(mi355_index* ix, const void* raw_vectors, uint32_t raw_dtype) try {
   if (!ix || !raw_vectors) return fail(MI355_ERR_INVALID_INPUT, "NULL argument");
+  if (ix->ivf_flat) return fail(MI355_ERR_INVALID_INPUT, "an IVF_FLAT index scans its own raw column: nothing can be attached");
   if (raw_dtype > MI355_DTYPE_F16) return fail(MI355_ERR_INVALID_INPUT, "bad raw_dtype enum");
   std::lock_guard<std::mutex> lk(ix->mu);
   HIP_TRY(hipSetDevice(ix->device));
@@ -579,6 +603,7 @@ extern "C" int32_t mi355_index_attach_raw(mi355_index* ix, const void* raw_vecto
 
 extern "C" int32_t mi355_index_detach_raw(mi355_index* ix) try {
   if (!ix) return fail(MI355_ERR_INVALID_INPUT, "index is NULL");
+  if (ix->ivf_flat) return fail(MI355_ERR_INVALID_INPUT, "an IVF_FLAT index scans its own raw column: nothing can be detached");
   std::lock_guard<std::mutex> lk(ix->mu);
   HIP_TRY(hipSetDevice(ix->device));
   ST_TRY(join_exchange(ix));

@@ -373,7 +373,8 @@ static int32_t search_locked(mi355_index* ix, const std::vector<SearchCall>& all
     d_cnt_ann = cnt2.as<uint32_t>();
   }
   // latency mode: small host batches without profiling / prefilter / external probes replay a graph
-  const bool graphable = ix->use_graph && host_io && n_queries <= 64 && (ix->profile & MI355_PROFILE_MASK) == 0 &&
+  // (IVF_FLAT handles always launch eagerly: MI355_CFG_GRAPH is ignored for them, include/mi355_ann.h)
+  const bool graphable = ix->use_graph && !ix->ivf_flat && host_io && n_queries <= 64 && (ix->profile & MI355_PROFILE_MASK) == 0 &&
                          !ext_probes && pl.filter.mode == MI355_FILTER_NONE;
   bool used_graph = false;
   if (graphable)
@@ -456,6 +457,8 @@ static int32_t search_impl(mi355_index* ix, const float* queries, uint32_t n_que
                            const mi355_search_params* p, const uint64_t* ext_probes, uint32_t ext_nprobe,
                            uint64_t* out_rowids, float* out_dist, uint32_t* out_counts) {
   const auto t_entry = std::chrono::steady_clock::now();
+  mi355_search_params p_flat;
+  p = ivf_flat_params(ix, p, &p_flat);  // (lives until this call returns: coalesced peers compare against it meanwhile)
   SearchShape sh;
   ST_TRY(check_search(ix, queries, n_queries, p, ext_probes, ext_nprobe, out_rowids, out_dist, out_counts, &sh, false));
   if (n_queries == 0) return MI355_OK;

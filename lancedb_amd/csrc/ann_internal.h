@@ -7,6 +7,7 @@
 //   ann_index_search.hip  call driver: request checks, coalescing queue, graph cache, host I/O, mi355_search*
 //   ann_scan_skew*.hip    launchers / instantiations of the production scan kernel (plain and padded / multi-slab)
 //   ann_scan_pair.hip     launcher of the generic scan kernel (4-bit codes, MI355_INDEX_GENERIC_SCAN)
+//   ann_scan_ivf_flat.hip launcher of the IVF_FLAT scan (exact distances over raw rows, MI355_INDEX_IVF_FLAT)
 //   ann_flat.hip          flat handle: open / search (MFMA filter + exact re-rank)
 //   ann_build.hip   index training and population
 //   ann_comm.hip    RCCL exchange behind the ABI: mi355_comm_*, mi355_search_sharded
@@ -214,6 +215,9 @@ struct mi355_index {
   // device data
   DevBuf centroids, cnorm, codebook, codes, code_off, plen, pstride, lrow0, grow0, row_ids, raw;
   bool has_row_ids = false, has_raw = false, local_arrays = false;
+  // MI355_INDEX_IVF_FLAT: no PQ stage, the raw column (`raw`, or the caller's borrowed device column) is scanned
+  bool ivf_flat = false;
+  const void* raw_borrowed = nullptr;
   uint32_t raw_dtype = 0;
   const void* raw_attached = nullptr;  // mi355_index_attach_raw: borrowed device column (local row order)
   uint32_t raw_attached_dtype = 0;
@@ -221,7 +225,8 @@ struct mi355_index {
   const void* raw_mapped_dev = nullptr;
   std::vector<uint64_t> raw_row_of_local;  // unused unless mapped (see ann_index.hip)
   std::vector<uint32_t> h_plen;
-  // code layout: MI355_SCAN_PAIR = [mb][pstride] blocks, MI355_SCAN_SKEW = pre-skewed streams
+  // code layout: MI355_SCAN_PAIR = [mb][pstride] blocks, MI355_SCAN_SKEW = pre-skewed streams, MI355_SCAN_IVF_FLAT = none
+  // (raw rows in local order)
   uint32_t layout = MI355_SCAN_PAIR;
   uint32_t n_cus = 256;
   bool merge_block_tried = false, merge_block_ok = false;  // k_merge_cands<KPL, 16> may use MERGE_BLOCK_LDS bytes
@@ -330,6 +335,16 @@ int32_t arm_deadline(mi355_index* ix, uint32_t timeout_ms, hipStream_t st);
 // scan launchers (ann_scan_pair.hip / ann_scan_skew.hip)
 struct ScanArgs;
 struct SkewArgs;
+struct IvfFlatArgs;
+int32_t launch_scan_ivf_flat(const IvfFlatArgs& a, uint32_t nq, hipStream_t st);
+// an IVF_FLAT handle ignores refine_factor (its distances are exact already): the params of the call without it
+static inline const mi355_search_params* ivf_flat_params(const mi355_index* ix, const mi355_search_params* p,
+                                                         mi355_search_params* tmp) {
+  if (!ix || !ix->ivf_flat || !p || p->struct_size != sizeof(mi355_search_params) || !p->refine_factor) return p;
+  *tmp = *p;
+  tmp->refine_factor = 0;
+  return tmp;
+}
 int32_t launch_scan_pair(const ScanArgs& sa, dim3 grid, hipStream_t st, uint32_t vpt, uint32_t nt);
 size_t scan_pair_lds(uint32_t m, uint32_t nbits, uint32_t dim, uint32_t lr, uint32_t nt);
 uint32_t scan_pair_m_lds(uint32_t m, uint32_t nbits, uint32_t dim);

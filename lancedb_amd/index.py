@@ -259,6 +259,67 @@ class IvfPqIndex(_Handle):
         return _run_search(fn, self._h, self.dim, queries, p, out)
 
 
+class IvfFlatIndex(IvfPqIndex):
+    """An IVF_FLAT index resident on one MI355X (Index::IvfFlat, rust/lancedb/src/index.rs:80; builder
+    index/vector.rs:170-210): IVF partitions over the RAW rows, no PQ stage.  A search picks exactly the
+    probes an IVF-PQ index with the same centroids and metric picks, and returns the exact (flat-search)
+    distances of the rows of those partitions.
+
+    `centroids` [nlist, dim] f32, `part_offsets` [nlist+1], `raw_vectors` [n, dim] (f32 / bf16 / f16 per
+    `raw_dtype`) and optional `row_ids` in index order (ivf_flat_assign's order).  A device `raw_vectors`
+    of an unsharded handle is scanned where it is (the handle keeps a reference to it); host arrays are
+    copied to HBM.  Same search / search_probes / coarse_topn / stats / configure surface as IvfPqIndex;
+    refine_factor is accepted and changes nothing (the distances are exact)."""
+
+    def __init__(self, centroids, part_offsets, raw_vectors, row_ids=None, metric="l2", raw_dtype=_abi.DTYPE_F32,
+                 device=0, shard_count=1, shard_rank=0, local_arrays=False, part_owner=None):
+        _Handle.__init__(self)
+        if raw_vectors is None:
+            raise ValueError("an IVF_FLAT index needs raw_vectors (the rows it scans)")
+        on_dev = _is_device(raw_vectors)
+        po = np.ascontiguousarray(part_offsets, dtype=np.uint64)  # always host
+        if on_dev:
+            cen, rid, raw = centroids, row_ids, raw_vectors.contiguous()
+        else:
+            cen = _host(centroids, np.float32)
+            rid = _host(row_ids, np.uint64)
+            raw = np.ascontiguousarray(raw_vectors)
+            if raw_dtype == _abi.DTYPE_F32:
+                raw = np.ascontiguousarray(raw, dtype=np.float32)
+        nlist, dim = cen.shape
+        self.dim, self.nlist, self.m, self.nbits = int(dim), int(nlist), 0, 0
+        self.metric = _abi.METRIC_NAMES[metric] if isinstance(metric, str) else int(metric)
+        d = _abi.IndexDesc()
+        d.struct_size = C.sizeof(_abi.IndexDesc)
+        d.dim, d.nlist, d.m, d.nbits = self.dim, self.nlist, 0, 0
+        d.flags = _abi.INDEX_IVF_FLAT | (_abi.INDEX_LOCAL_ARRAYS if local_arrays else 0)
+        d.metric = self.metric
+        d.n_rows = int(po[-1])
+        d.mem = _abi.MEM_DEVICE if on_dev else _abi.MEM_HOST
+        d.centroids, d.codebook, d.part_offsets = _ptr(cen), None, _ptr(po)
+        d.codes, d.row_ids, d.raw_vectors = None, _ptr(rid), _ptr(raw)
+        d.raw_dtype = raw_dtype
+        d.device = device
+        d.shard_count, d.shard_rank = shard_count, shard_rank
+        if part_owner is not None:
+            self._owner = np.ascontiguousarray(part_owner, dtype=np.uint32)
+            if self._owner.shape != (int(d.nlist),):
+                raise ValueError("part_owner must be [nlist]")
+            d.part_owner = self._owner.ctypes.data_as(C.c_void_p)
+        self.n_rows = d.n_rows
+        self.raw_dtype = raw_dtype
+        self._keep = [cen, po, rid, raw]
+        check(lib().mi355_index_open(C.byref(d), C.byref(self._h)))
+        # a device column the handle scans in place must outlive it; everything else was copied
+        self._keep = [raw] if on_dev else []
+
+    def attach_raw_vectors(self, raw, raw_dtype=_abi.DTYPE_F32):
+        check(lib().mi355_index_attach_raw(self._h, _ptr(raw), C.c_uint32(raw_dtype)))  # InvalidInput: the column is the index
+
+    def detach_raw_vectors(self):
+        check(lib().mi355_index_detach_raw(self._h))
+
+
 class FlatIndex(_Handle):
     """A raw vector column on the GPU for exhaustive search
     (bypass_vector_index, rust/lancedb/src/query.rs:1360-1370)."""
@@ -414,6 +475,30 @@ def ivfpq_encode(vectors, centroids, codebook, metric="l2", device=0, return_ass
     check(lib().mi355_ivfpq_encode(C.byref(desc), _ptr(vectors), C.c_uint64(n), _ptr(po), _ptr(codes), _ptr(order),
                                    _ptr(assign) if return_assign else None))
     return (po, codes, order, assign) if return_assign else (po, codes, order)
+
+
+def ivf_flat_assign(vectors, centroids, metric="l2", device=0, return_assign=False):
+    """Population of an IVF_FLAT index: mi355_ivfpq_encode in its assign-only mode (m = 0, no codebook, no codes).
+    Every row of `vectors` [n, dim] f32 goes to its IVF partition and the rows are laid out partition by partition,
+    exactly as ivfpq_encode does for the same centroids.  Host arrays only.
+    -> (part_offsets [nlist+1] u64, order [n] u64 [, assign [n] u32]): IvfFlatIndex takes raw_vectors = vectors[order],
+    row_ids = ids[order]."""
+    if _is_device(vectors) or _is_device(centroids):
+        raise ValueError("ivf_flat_assign takes host arrays")
+    vectors, centroids = _host(vectors, np.float32), _host(centroids, np.float32)
+    n, dim = int(vectors.shape[0]), int(vectors.shape[1])
+    nlist = int(centroids.shape[0])
+    if tuple(centroids.shape) != (nlist, dim) or nlist == 0:
+        raise ValueError("centroids must be [nlist, dim]")
+    mcode = _abi.METRIC_NAMES[metric] if isinstance(metric, str) else int(metric)
+    po = np.zeros(nlist + 1, dtype=np.uint64)
+    order = np.empty(n, dtype=np.uint64)
+    assign = np.empty(n, dtype=np.uint32)
+    desc = _abi.EncodeDesc(struct_size=C.sizeof(_abi.EncodeDesc), dim=dim, nlist=nlist, m=0, nbits=0, metric=mcode,
+                           mem=_abi.MEM_HOST, device=device, centroids=_ptr(centroids), codebook=None)
+    check(lib().mi355_ivfpq_encode(C.byref(desc), _ptr(vectors), C.c_uint64(n), _ptr(po), None, _ptr(order),
+                                   _ptr(assign) if return_assign else None))
+    return (po, order, assign) if return_assign else (po, order)
 
 
 def _kmeans_desc(dim, k, metric, iters, ld, dev_in, dev_index):

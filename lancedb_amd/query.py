@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _abi
 from ._lib import InvalidInput, QueryTimeout
-from .index import FlatIndex, IvfPqIndex
+from .index import FlatIndex, IvfFlatIndex, IvfPqIndex
 
 DEFAULT_TOP_K = 10  # rust/lancedb/src/query.rs:36
 
@@ -311,8 +311,9 @@ class VectorTable:
 
     def __init__(self, index: Optional[IvfPqIndex] = None, flat: Optional[FlatIndex] = None,
                  index_metric: Optional[str] = None):
+        """`index`: an IvfPqIndex or an IvfFlatIndex (a subclass: the same search surface)."""
         if index is None and flat is None:
-            raise InvalidInput(1, "VectorTable needs an IvfPqIndex and/or a FlatIndex")
+            raise InvalidInput(1, "VectorTable needs an IvfPqIndex / IvfFlatIndex and/or a FlatIndex")
         self.index, self.flat = index, flat
         self.dim = index.dim if index is not None else flat.dim
 
@@ -400,15 +401,16 @@ class VectorPlan:
         if (r.allow_rowids is not None or r.block_rowids is not None) and not self.prefilter:
             lines.append("  FilterExec: postfilter on _rowid" + m(output_rows=rows))
         if self.use_index:
-            kk = self.k * (r.refine_factor or 1)
-            if r.refine_factor:
+            ivf_flat = isinstance(self.table.index, IvfFlatIndex)  # exact distances already: refine_factor changes nothing
+            kk = self.k * (1 if ivf_flat else (r.refine_factor or 1))
+            if r.refine_factor and not ivf_flat:
                 lines.append(f"  SortExec: TopK(fetch={self.k}), expr=[_distance ASC NULLS LAST, _rowid ASC NULLS LAST]" + m(output_rows=rows))
                 lines.append("    KNNVectorDistance: refine, metric=" + (r.distance_type or "index")
                              + m(us("refine"), rows_reranked=nq * kk if metrics is not None else None))
                 lines.append("      Take: raw vectors of k * refine_factor = %d rows" % kk)
             lines.append(f"  SortExec: TopK(fetch={kk}), expr=[_distance ASC NULLS LAST, _rowid ASC NULLS LAST]"
                          + m(us("merge"), candidate_lists=st.get("work_items")))
-            lines.append(f"    ANNSubIndex: name=mi355_ivf_pq, k={kk}, deltas=1"
+            lines.append(f"    ANNSubIndex: name={'mi355_ivf_flat' if ivf_flat else 'mi355_ivf_pq'}, k={kk}, deltas=1"
                          + (", prefilter=rowid mask" if self.prefilter and (r.allow_rowids is not None or r.block_rowids is not None) else "")
                          + m(us("scan"), rows_scanned=st.get("vectors_scanned"), bytes_read=st.get("code_bytes_scanned"),
                              work_items=st.get("work_items"), scan_variant=st.get("scan_variant"), timed_out=st.get("timed_out")))
