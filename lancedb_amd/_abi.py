@@ -135,6 +135,35 @@ class FlatDesc(C.Structure):
     ]
 
 
+class MultivecDesc(C.Structure):  # include/mi355_multivec.h
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dim", C.c_uint32),
+        ("n_rows", C.c_uint64),
+        ("n_vectors", C.c_uint64),
+        ("dtype", C.c_uint32),
+        ("mem", C.c_uint32),
+        ("vectors", C.c_void_p),
+        ("offsets", C.c_void_p),
+        ("row_ids", C.c_void_p),
+        ("metric", C.c_uint32),
+        ("device", C.c_int32),
+    ]
+
+
+MULTIVEC_MAX_QVEC = 1024
+
+# the entry points of the companion header include/mi355_multivec.h (same library; EXPORTED_SYMBOLS is mi355_ann.h's)
+MULTIVEC_SYMBOLS = (
+    "mi355_multivec_open",
+    "mi355_multivec_close",
+    "mi355_multivec_set_stream",
+    "mi355_multivec_sync",
+    "mi355_multivec_info",
+    "mi355_multivec_search",
+)
+
+
 class EncodeDesc(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),

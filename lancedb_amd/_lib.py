@@ -21,6 +21,8 @@ _OBJ = os.path.join(_PKG, "build")
 _UNITS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".hip"))
 _HEADERS = sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".h", ".inc")))
 _HEADER = os.path.join(ROOT, "include", "mi355_ann.h")
+# every public header (mi355_ann.h and its companions) is a dependency of every unit
+_PUBLIC_HEADERS = sorted(os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -77,7 +79,7 @@ def _newer(path, deps):
 
 def _stale():
     srcs = [os.path.join(_CSRC, u) for u in _UNITS]
-    return _newer(LIB_PATH, srcs + _HEADERS + [_HEADER])
+    return _newer(LIB_PATH, srcs + _HEADERS + _PUBLIC_HEADERS)
 
 
 def build(force=False, verbose=False, extra_flags=(), lib_path=None, obj_dir=None):
@@ -94,7 +96,7 @@ def build(force=False, verbose=False, extra_flags=(), lib_path=None, obj_dir=Non
     for u in _UNITS:
         src = os.path.join(_CSRC, u)
         obj = os.path.join(obj_dir, u[:-4] + ".o")
-        if force or extra_flags or _newer(obj, [src] + _HEADERS + [_HEADER]):
+        if force or extra_flags or _newer(obj, [src] + _HEADERS + _PUBLIC_HEADERS):
             cmd = [hipcc] + HIPCC_FLAGS + list(extra_flags) + ["-c", src, "-o", obj]
             jobs.append((u, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     failed = []
@@ -159,7 +161,7 @@ def lib():
         _bind_hip_runtime()
         L = C.CDLL(LIB_PATH)
         L.mi355_abi_version.restype = C.c_uint32
-        for name in _abi.EXPORTED_SYMBOLS:
+        for name in _abi.EXPORTED_SYMBOLS + _abi.MULTIVEC_SYMBOLS:
             if name != "mi355_abi_version":
                 getattr(L, name).restype = C.c_int32
         if L.mi355_abi_version() != _abi.ABI_VERSION:

@@ -9,6 +9,7 @@
 //   ann_scan_pair.hip     launcher of the generic scan kernel (4-bit codes, MI355_INDEX_GENERIC_SCAN)
 //   ann_scan_ivf_flat.hip launcher of the IVF_FLAT scan (exact distances over raw rows, MI355_INDEX_IVF_FLAT)
 //   ann_flat.hip          flat handle: open / search (MFMA filter + exact re-rank)
+//   ann_multivec.hip      multivector handle (List<FixedSizeList> columns): exact late-interaction search
 //   ann_build.hip   index training and population
 //   ann_comm.hip    RCCL exchange behind the ABI: mi355_comm_*, mi355_search_sharded
 #pragma once

@@ -403,6 +403,127 @@ class FlatIndex(_Handle):
         return _run_search(lib().mi355_flat_search, self._h, self.dim, queries, p, out)
 
 
+def multivector_from_arrow(arr):
+    """A pyarrow ListArray / LargeListArray (or ChunkedArray of them) of FixedSizeList<float16 | float32 | float64>
+    -> (values [n_vectors, dim] float16 / float32, offsets [n_rows + 1] uint64, dtype MI355_DTYPE_*): the arrays
+    mi355_multivec_open takes.  Null rows become empty rows (never returned by a search).  float64 values are
+    NARROWED to float32 (the engine's element types are f32 / bf16 / f16).  Pure host code: no device needed."""
+    import pyarrow as pa
+    from ._lib import InvalidInput
+    if isinstance(arr, pa.ChunkedArray):
+        arr = arr.combine_chunks() if arr.num_chunks != 1 else arr.chunk(0)
+    t = arr.type
+    if not (pa.types.is_list(t) or pa.types.is_large_list(t)) or not pa.types.is_fixed_size_list(t.value_type):
+        raise InvalidInput(1, f"a multivector column is List<FixedSizeList<float>>, not {t}")
+    vt = t.value_type.value_type
+    if vt == pa.float16():
+        np_dt, dtype = np.float16, _abi.DTYPE_F16
+    elif vt in (pa.float32(), pa.float64()):
+        np_dt, dtype = np.float32, _abi.DTYPE_F32
+    else:
+        raise InvalidInput(1, f"multivector elements must be float16 / float32 / float64, not {vt}")
+    dim = t.value_type.list_size
+    n = len(arr)
+    off = np.asarray(arr.offsets, dtype=np.int64)  # (len n + 1, already shifted by a slice's offset)
+    valid = np.ones(n, dtype=bool) if arr.null_count == 0 else ~np.asarray(arr.is_null(), dtype=bool)
+    lens = np.where(valid, np.diff(off), 0)
+    # the child FixedSizeList's flat values (`values` ignores a slice offset: a sliced child starts at child.offset)
+    child = arr.values
+    flat = np.asarray(child.values.to_numpy(zero_copy_only=False))[child.offset * dim:(child.offset + len(child)) * dim]
+    flat = flat.reshape(-1, dim)
+    keep = np.repeat(valid, np.diff(off))
+    vec = flat[off[0]:off[-1]][keep]
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(lens, out=offsets[1:])
+    return np.ascontiguousarray(vec, dtype=np_dt), offsets, dtype
+
+
+class MultiVectorFlat(_Handle):
+    """A multivector column (List<FixedSizeList<float, dim>>: ColBERT / ColPali late-interaction embeddings) on the
+    GPU for exact search (include/mi355_ann.h mi355_multivec_*): per query set, the rows with the smallest
+    sum over its vectors of the minimum cosine distance to the row's vectors (n_qvec - sum of MaxSim).
+
+    `vectors` [n_vectors, dim] (f32 / bf16 / f16 per `dtype`), `offsets` [n_rows + 1] (Arrow list offsets,
+    offsets[0] = 0), optional `row_ids` [n_rows].  Host arrays are copied to HBM; device tensors are scanned where
+    they are (the handle keeps a reference).  Cosine only: metric "cosine" or None."""
+    _close_fn = "mi355_multivec_close"
+
+    def __init__(self, vectors, offsets, row_ids=None, dtype=_abi.DTYPE_F32, device=0, metric="cosine"):
+        super().__init__()
+        on_dev = _is_device(vectors)
+        if on_dev:
+            v, off, rid = vectors.contiguous(), offsets.contiguous(), None if row_ids is None else row_ids.contiguous()
+            n_rows = int(off.shape[0]) - 1
+        else:
+            v = np.ascontiguousarray(vectors)
+            if dtype == _abi.DTYPE_F32:
+                v = np.ascontiguousarray(v, dtype=np.float32)
+            off = np.ascontiguousarray(offsets, dtype=np.uint64)
+            rid = _host(row_ids, np.uint64)
+            n_rows = int(off.shape[0]) - 1
+        if len(v.shape) != 2 or n_rows < 0:
+            raise ValueError("vectors must be [n_vectors, dim] and offsets [n_rows + 1]")
+        self.dim, self.n_rows, self.n_vectors = int(v.shape[1]), n_rows, int(v.shape[0])
+        self.metric = _abi.METRIC_DEFAULT if metric is None else (
+            _abi.METRIC_NAMES[metric] if isinstance(metric, str) else int(metric))
+        d = _abi.MultivecDesc()
+        d.struct_size = C.sizeof(_abi.MultivecDesc)
+        d.dim, d.n_rows, d.n_vectors, d.dtype = self.dim, self.n_rows, self.n_vectors, dtype
+        d.mem = _abi.MEM_DEVICE if on_dev else _abi.MEM_HOST
+        d.vectors, d.offsets, d.row_ids = _ptr(v), _ptr(off), _ptr(rid)
+        d.metric, d.device = self.metric, device
+        check(lib().mi355_multivec_open(C.byref(d), C.byref(self._h)))
+        # a device column the handle scans in place must outlive it; everything else was copied
+        self._keep = [v] if on_dev else []
+
+    @classmethod
+    def from_arrow(cls, arr, row_ids=None, device=0):
+        """Open a handle over a pyarrow List / LargeList<FixedSizeList<float16 | float32 | float64>> column
+        (multivector_from_arrow: null rows are empty, float64 is narrowed to float32)."""
+        vec, off, dtype = multivector_from_arrow(arr)
+        return cls(vec, off, row_ids=row_ids, dtype=dtype, device=device)
+
+    def set_stream(self, hip_stream):
+        check(lib().mi355_multivec_set_stream(self._h, C.c_void_p(hip_stream or 0)))
+
+    def sync(self):
+        check(lib().mi355_multivec_sync(self._h))
+
+    def info(self):
+        """-> (rows, stored vectors)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        check(lib().mi355_multivec_info(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def search(self, queries, params=None, out=None, **kw):
+        """`queries`: ONE query set [n_qvec, dim] (a [dim] vector is a set of one) or a batch [B, n_qvec, dim] of
+        equal-length sets.  -> SearchResult with one row per query set (B rows; 1 for a single set)."""
+        p = params if params is not None else _abi.make_params(**kw)
+        if _is_device(queries):
+            q = queries.contiguous()
+            q = q.view(1, 1, -1) if len(q.shape) == 1 else q.view(1, *q.shape) if len(q.shape) == 2 else q
+        else:
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+            q = q.reshape(1, 1, -1) if q.ndim == 1 else q[None] if q.ndim == 2 else q
+        if len(q.shape) != 3 or int(q.shape[2]) != self.dim:
+            raise ValueError(f"queries must be [n_qvec, {self.dim}] or [B, n_qvec, {self.dim}], got {tuple(q.shape)}")
+        nb, n_qvec, k = int(q.shape[0]), int(q.shape[1]), p.k
+        fn = lib().mi355_multivec_search
+        if _is_device(q):
+            if out is None:
+                ids, dist, cnt = _device_empty_like(q, [((nb, k), "int64"), ((nb, k), "float32"), ((nb,), "int32")])
+            else:
+                ids, dist, cnt = out
+            p.io_mem = _abi.MEM_DEVICE
+        else:
+            ids = np.empty((nb, k), dtype=np.uint64)
+            dist = np.empty((nb, k), dtype=np.float32)
+            cnt = np.zeros(nb, dtype=np.uint32)
+            p.io_mem = _abi.MEM_HOST
+        check(fn(self._h, _ptr(q), C.c_uint32(nb), C.c_uint32(n_qvec), C.byref(p), _ptr(ids), _ptr(dist), _ptr(cnt)))
+        return SearchResult(ids, dist, cnt)
+
+
 def merge_topk(in_rowids, in_dist, in_counts, k, stream=0):
     """Device-side k-way merge of [n_lists, nq, k] candidate lists (device
     arrays: torch tensors or DeviceArray): the reducer after the multi-GPU

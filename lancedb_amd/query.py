@@ -15,8 +15,8 @@ from typing import Any, Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi
-from ._lib import InvalidInput, QueryTimeout
-from .index import FlatIndex, IvfFlatIndex, IvfPqIndex
+from ._lib import InvalidInput, NotSupported, QueryTimeout
+from .index import FlatIndex, IvfFlatIndex, IvfPqIndex, MultiVectorFlat
 
 DEFAULT_TOP_K = 10  # rust/lancedb/src/query.rs:36
 
@@ -311,9 +311,13 @@ class VectorTable:
 
     def __init__(self, index: Optional[IvfPqIndex] = None, flat: Optional[FlatIndex] = None,
                  index_metric: Optional[str] = None):
-        """`index`: an IvfPqIndex or an IvfFlatIndex (a subclass: the same search surface)."""
+        """`index`: an IvfPqIndex or an IvfFlatIndex (a subclass: the same search surface).  `flat`: a FlatIndex, or a
+        MultiVectorFlat for a multivector (List<FixedSizeList>) column — searched exactly, with no index."""
         if index is None and flat is None:
-            raise InvalidInput(1, "VectorTable needs an IvfPqIndex / IvfFlatIndex and/or a FlatIndex")
+            raise InvalidInput(1, "VectorTable needs an IvfPqIndex / IvfFlatIndex and/or a FlatIndex / MultiVectorFlat")
+        self.multivector = isinstance(flat, MultiVectorFlat)
+        if self.multivector and index is not None:
+            raise NotSupported(4, "indexes over a multivector column are not supported: search it without an index")
         self.index, self.flat = index, flat
         self.dim = index.dim if index is not None else flat.dim
 
@@ -327,8 +331,11 @@ class VectorTable:
 
     def query_nearest_to(self, vector):  # Query::nearest_to, query.rs:1011-1021
         q = VectorQuery(self)
-        a = np.asarray(vector)
-        vecs = [a] if a.ndim == 1 else list(a)  # a list of vectors = multi-vector query
+        if getattr(self, "multivector", False) and isinstance(vector, (list, tuple)) and len(vector) and np.ndim(vector[0]) == 1:
+            vecs = [np.asarray(v) for v in vector]  # (the vectors of a multivector query may disagree in length)
+        else:
+            a = np.asarray(vector)
+            vecs = [a] if a.ndim == 1 else list(a)  # a list of vectors = multi-vector query
         if len(vecs) == 0:  # ensure_vector_query, python/python/lancedb/query.py:332-350
             raise InvalidInput(1, "Vector query must be a non-empty list")
         for v in vecs:
@@ -424,7 +431,11 @@ class VectorPlan:
                          + m(float(st.get("us_gemm", 0.0)) if "us_gemm" in st else None, flops=st.get("gemm_flops"),
                              gemm_variant=st.get("gemm_variant")))
             lines.append("      LanceRead: raw column resident in HBM")
-        if len(self.queries) > 1:  # create_multi_vector_plan (table/query.rs:334-381)
+        if self.multivector:  # ONE query of n_qvec vectors (table/query.rs:169-199): no union, no query_index
+            lines[-2] = lines[-2].replace("KNNVectorDistance: metric=" + (r.distance_type or "l2"),
+                                          f"KNNVectorDistance: multivector, metric=cosine, n_qvec={nq}")
+            lines[-1] = "      LanceRead: multivector column resident in HBM"
+        elif len(self.queries) > 1:  # create_multi_vector_plan (table/query.rs:334-381)
             lines = ["UnionExec / query_index: %d query vectors in ONE device batch" % len(self.queries)] + ["  " + ln for ln in lines]
         if metrics is not None:
             lines = [f"AnalyzeExec verbose=true, elapsed={metrics.get('elapsed_s', 0.0) * 1e6:.1f}us, metrics=[output_rows={rows}]"] + \
@@ -434,8 +445,12 @@ class VectorPlan:
                          f"refine_factor={self.params.refine_factor} timeout_ms={self.params.timeout_ms}")
         return "\n".join(lines)
 
+    @property
+    def multivector(self):
+        return getattr(self.table, "multivector", False)
+
     def output_columns(self):
-        cols = ["_rowid", "_distance"] + (["query_index"] if len(self.queries) > 1 else [])
+        cols = ["_rowid", "_distance"] + (["query_index"] if len(self.queries) > 1 and not self.multivector else [])
         sel = self.request.select
         if sel is not None:
             unknown = [c for c in sel if c not in cols]
@@ -568,7 +583,7 @@ def execute_generic_query(table, req: VectorQueryRequest, options: QueryExecutio
     res = table.index.search(q, plan.params) if plan.use_index else table.flat.search(q, plan.params)
     filtered = req.allow_rowids is not None or req.block_rowids is not None
     rid, dist, qidx = [], [], []
-    for i in range(q.shape[0]):
+    for i in range(len(res.counts)):  # (a multivector query is ONE query set: one result row)
         n = int(res.counts[i])
         r, d = res.rowids[i, :n], res.distances[i, :n]
         if filtered and not plan.prefilter:  # postfilter: the predicate thins out the k results
@@ -578,7 +593,7 @@ def execute_generic_query(table, req: VectorQueryRequest, options: QueryExecutio
         dist.append(d[offset:])
         qidx.append(np.full(max(len(r) - offset, 0), i, dtype=np.int32))
     out = {"_rowid": np.concatenate(rid), "_distance": np.concatenate(dist)}
-    if q.shape[0] > 1:
+    if len(res.counts) > 1:
         out["query_index"] = np.concatenate(qidx)
     if req.order_by:
         out = _order_by(out, req.order_by)

@@ -134,7 +134,9 @@ def response_from_ipc(data: bytes) -> dict:
 
 def handle_query(table, body, allow_rowids=None, block_rowids=None):
     """POST /v1/table/<name>/query/ without the HTTP: -> (content type, Arrow IPC file bytes).
-    `allow_rowids` / `block_rowids`: the evaluated `filter` of the body, if it had one."""
+    `allow_rowids` / `block_rowids`: the evaluated `filter` of the body, if it had one.  On a table over a multivector
+    column a `vector` that is a list of vectors is ONE query of that many vectors (table/query.rs:169-199): one result
+    set, no query_index."""
     if isinstance(body, (bytes, bytearray, str)):
         body = json.loads(body)
     had_filter = bool(body.get("filter"))

@@ -15,6 +15,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mi355_ann.h")
 OUT = os.path.join(ROOT, "integration", "mi355_sys.rs")
+# the companion header of multivector columns and its module (same library, generated the same way)
+MV_HEADER = os.path.join(ROOT, "include", "mi355_multivec.h")
+MV_OUT = os.path.join(ROOT, "integration", "mi355_multivec_sys.rs")
 
 PRIM = {"uint8_t": "u8", "uint32_t": "u32", "int32_t": "i32", "uint64_t": "u64", "int64_t": "i64", "float": "f32", "double": "f64",
         "size_t": "usize", "char": "c_char", "void": "c_void"}
@@ -163,15 +166,66 @@ def generate():
     return "\n".join(o) + "\n"
 
 
+def generate_multivec():
+    """integration/mi355_multivec_sys.rs from include/mi355_multivec.h: its constants, handle, descriptor and entry
+    points; the types it shares with mi355_ann.h (mi355_search_params) come from the mi355_sys module."""
+    base = parse(open(HEADER).read())
+    consts, structs, opaque, funcs, known = parse(open(MV_HEADER).read())
+    shared = sorted({t for _, _, params in funcs for _, ct in params for t in re.findall(r"\w+", ct)} & set(base[1]))
+    known = known | base[4]
+    o = []
+    w = o.append
+    w("// mi355_multivec_sys.rs — GENERATED from include/mi355_multivec.h by scripts/gen_rust_sys.py; do not edit by hand.")
+    w("// Raw `extern \"C\"` bindings of the multivector entry points of libmi355_ann.so (INTEGRATION.md §3, multivector")
+    w("// columns), beside mi355_sys.rs.  Checked against the header by tests/test_multivec_abi.py: identical function set,")
+    w("// argument counts, struct field order, field offsets and sizes.")
+    w("#![allow(non_camel_case_types, non_upper_case_globals, dead_code)]")
+    w("use core::ffi::c_void;")
+    if shared:
+        w(f"use super::mi355_sys::{{{', '.join(shared)}}};")
+    w("")
+    w(f"// ---- constants ({len(consts)})")
+    for name, val in consts:
+        w(f"pub const {name}: u32 = {val};")
+    w("")
+    w("// ---- opaque handles")
+    for name in opaque:
+        w("#[repr(C)]")
+        w(f"pub struct {name} {{")
+        w("    _private: [u8; 0],")
+        w("}")
+    w("")
+    w("// ---- descriptors (plain old data, `struct_size` = size_of::<Self>() as u32)")
+    for name, fields in structs.items():
+        w("#[repr(C)]")
+        w("#[derive(Clone, Copy)]")
+        w(f"pub struct {name} {{")
+        for fname, ctype, arr in fields:
+            rt = rust_type(ctype, known)
+            if arr:
+                rt = f"[{rt}; {arr}]"
+            w(f"    pub {fname}: {rt},")
+        w("}")
+    w("")
+    w(f"// ---- entry points ({len(funcs)}); statuses as in mi355_sys.rs (status_to_error there)")
+    w('#[link(name = "mi355_ann")]')
+    w('extern "C" {')
+    for name, ret, params in funcs:
+        ps = ", ".join(f"{pn}: {rust_type(pt, known)}" for pn, pt in params)
+        w(f"    pub fn {name}({ps}) -> {PRIM[ret]};")
+    w("}")
+    return "\n".join(o) + "\n"
+
+
 if __name__ == "__main__":
-    text = generate()
+    outputs = ((OUT, generate()), (MV_OUT, generate_multivec()))
     if "--check" in sys.argv:
-        cur = open(OUT).read() if os.path.exists(OUT) else ""
-        if cur != text:
-            print("integration/mi355_sys.rs is stale: run python scripts/gen_rust_sys.py", file=sys.stderr)
-            sys.exit(1)
-        sys.exit(0)
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    with open(OUT, "w") as f:
-        f.write(text)
-    print("wrote", OUT, len(text.splitlines()), "lines")
+        stale = [path for path, text in outputs if (open(path).read() if os.path.exists(path) else "") != text]
+        for path in stale:
+            print(f"{os.path.relpath(path, ROOT)} is stale: run python scripts/gen_rust_sys.py", file=sys.stderr)
+        sys.exit(1 if stale else 0)
+    for path, text in outputs:
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text)
+        print("wrote", path, len(text.splitlines()), "lines")
